@@ -13,7 +13,14 @@ amplitude (single-layer 10x10 D=6 tensor network, fp32), MI355X.
   the data path, ONE RCCL all-gather of (mantissa, exponent) pairs at the join; strong scaling: ``value`` = the
   one-rank tree's FLOPs / max-over-ranks time.  (256 slices are not reachable with all-6 bonds; ``--sliced`` keeps
   round 1's 216 single-value slices of the sweep, ``--two-sided`` round 2's branch decomposition.)
-* N == 1 also reports: ``secondary`` (BASELINE configs #2, #3 as worded -- the compressed boundary-MPS sweep at a stated
+* A plain run (no ``--full``) does only what the headline needs: set up (with ``--tree auto``: both trees run untimed to
+  pick the one timed), warm up, time ``--steps`` steps (HIP events around the launches of >= 1e9 multiplications inside
+  the timed region give ``roofline``'s dominant kernel), write ``--dump-outputs DIR`` if given, print the line.
+  ``result`` is the last timed step's (mantissa, exponent) pair; ``--dump-outputs DIR`` writes the same pair as returned
+  by the timed path to ``DIR/mantissa.npy`` and ``DIR/exponent_log10.npy`` (seeded inputs: runs compare file by file).
+* ``--full`` adds everything else, each after the timed region: ``roofline.classes`` (one launch-by-launch pass with an
+  event pair around every launch), ``result``'s error against the stored fp64 oracle value, and at N == 1:
+  ``secondary`` (BASELINE configs #2, #3 as worded -- the compressed boundary-MPS sweep at a stated
   chi, on the headline's tensors -- and #5: circuit amplitude, DMRG2 matvec / local update / sweeps),
   ``scaling_projection`` (the busiest rank's share of the N = 2 / 4 / 8 jobs timed on this one GPU), ``cpu_baseline``, and
   ``split_products_f16x3``: the same contraction re-run with the OPT-IN join arithmetic (Options.join_arith = "f16x3":
@@ -23,8 +30,8 @@ amplitude (single-layer 10x10 D=6 tensor network, fp32), MI355X.
   then says so).
 
 Prints ONE JSON line on rank 0 (contract in the task statement) with the extra ``roofline`` (dominant kernel, HIP
-events on the launch stream) and ``cpu_baseline`` (numpy/OpenBLAS port of the sweep: a bounded sample to pick the thread
-count, then the WHOLE network once on this host, ~70 s) objects.
+events on the launch stream) and ``cpu_baseline`` (``--full`` only, else null: numpy/OpenBLAS port of the sweep: a
+bounded sample to pick the thread count, then the WHOLE network once on this host, ~70 s) objects.
 """
 
 import argparse
@@ -121,6 +128,11 @@ def cpu_baseline(D, Ly, seed, rows=3, repeats=5, Lx=10, full=True, full_budget_s
     except ImportError:      # no way to pin: report whatever the BLAS picked
         threadpool_limits = None
     cores = os.cpu_count() or 1
+    # the sweep stays within the CPUs this process may use (affinity, OMP_NUM_THREADS): on a shared host the core count
+    # is the machine's, and more BLAS threads than the allotment only slow the sample down
+    usable = len(os.sched_getaffinity(0)) if hasattr(os, "sched_getaffinity") else cores
+    if os.environ.get("OMP_NUM_THREADS", "").isdigit() and int(os.environ["OMP_NUM_THREADS"]) > 0:
+        usable = min(usable, int(os.environ["OMP_NUM_THREADS"]))
 
     def sample(nrows):
         arrays, inputs = tn2d_rand(nrows, Ly, D, seed=seed, dtype="float32")
@@ -140,7 +152,7 @@ def cpu_baseline(D, Ly, seed, rows=3, repeats=5, Lx=10, full=True, full_budget_s
 
     small = sample(2)
     sweep = {}
-    for th in sorted({min(cores, t) for t in (16, 32, 64, cores)}):
+    for th in sorted({min(usable, t) for t in (16, 32, 64, usable)}):
         sweep[th] = run(small, th)
     best_th = min(sweep, key=sweep.get)
     big = sample(rows)
@@ -151,6 +163,7 @@ def cpu_baseline(D, Ly, seed, rows=3, repeats=5, Lx=10, full=True, full_budget_s
         "value": big[3] / med / 1e12,
         "unit": "TFLOP/s",
         "cores": cores,
+        "cores_usable": usable,
         "threads": best_th,
         "kind": "port",
         "sample": f"{rows}x{Ly} D={D} fp32 top-rows sweep of the same network ({big[3]:.3e} of the headline's FLOP), numpy "
@@ -323,6 +336,23 @@ def split_products_run(qa, dev, tree, xs, dtype, args, sync, ms_f32, flops_step,
         return {"error": f"{type(err).__name__}: {err}"}
 
 
+def dump_outputs(outdir, raw, res):
+    """``--dump-outputs DIR``: what the timed path returned in its last step, as a caller receives it -- the mantissa
+    array (in its own float dtype) and the base-10 exponent (float64) -- as ``DIR/mantissa.npy`` and
+    ``DIR/exponent_log10.npy``.  The inputs are seeded, so two builds run with the same arguments compare file by file."""
+    os.makedirs(outdir, exist_ok=True)
+    m = raw[0]
+    if hasattr(m, "to_numpy"):
+        m = m.to_numpy()
+    elif hasattr(m, "cpu"):
+        m = m.detach().cpu().numpy()
+    m = np.asarray(m)
+    if m.dtype not in (np.float32, np.float64):
+        m = m.astype(np.float64)
+    np.save(os.path.join(outdir, "mantissa.npy"), m)
+    np.save(os.path.join(outdir, "exponent_log10.npy"), np.asarray(res[1], dtype=np.float64))
+
+
 def _time_steps(fn, n, sync):
     sync()
     t0 = time.perf_counter()
@@ -423,6 +453,13 @@ def main():
                          "(steps are enqueued back to back and the device never waits for the host; measured equal)")
     ap.add_argument("--emulate-world", type=int, default=0,
                     help="one GPU times ONE rank's share (the busiest) of a job over this many ranks -- no collective")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline: the per-class roofline pass, the secondary configs, the scaling "
+                         "projection, the f16x3 split products, the CPU baseline, the error against the stored fp64 oracle "
+                         "value (and, for graph-replayed modes, the untimed pass that times the dominant kernel).  Off: set "
+                         "up, warm up, time the steps, print the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned (mantissa, exponent) as DIR/<name>.npy")
     args = ap.parse_args()
 
     dry_run = os.environ.get("QAMD_BENCH_DRYRUN") == "1"
@@ -600,13 +637,16 @@ def main():
         res = step()
     fence()
     dt = time.perf_counter() - t0
+    last = res
     res = materialize(res)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, last, res)
     prof, dev.profile = dev.profile, None
     if prog_obj is not None and rank == 0:
         timing_on[0] = False
         prog_obj._timing_slot = None
         prof = [rec for k in range(args.steps) for rec in prog_obj.timings(k)]
-    if graphed:
+    if graphed and args.full:
         # (per-call arguments of the executor, not process state: slices / the share launch by launch for this one pass)
         if rank == 0:
             dev.profile_min_mults = 10**9
@@ -626,7 +666,7 @@ def main():
     # table (``roofline.achieved`` per step class).  Kept out of the timed region because an event pair costs
     # each of the ~60 tiny first-row launches ~10 us of queue time.
     prof_all = None
-    if rank == 0 and mode in ("single", "quadrants"):
+    if rank == 0 and mode in ("single", "quadrants") and args.full:
         # ... and on ONE stream (``lanes=False``, a per-call argument): with the four corner sweeps overlapping, an event pair
         # brackets a launch's share of a contended machine, not the kernel -- the table prices every class with the chip to
         # itself
@@ -687,7 +727,7 @@ def main():
         value = flops_step / (dt / args.steps) / 1e12
         # ---- dominant kernel from HIP-event timings over the timed region ------
         agg = {}
-        for spec, dt_, name, sk, e0, e1 in prof:
+        for spec, dt_, name, sk, e0, e1 in prof or ():     # (none: a graph-replayed mode without --full)
             shape, nbytes, nflops = _launch_work(spec)
             # (the second join carries the closing inner product in its epilogue -- "<name> + dot", the DOT instantiation of
             # the same kernel on the same GEMM: one class with the plain launches)
@@ -773,7 +813,7 @@ def main():
             return (t_ * 1e3, rep_) if with_report else t_ * 1e3
 
         secondary = projection = None
-        if mode == "single" and not args.no_secondary and (args.Lx, args.Ly) == (10, 10):
+        if args.full and mode == "single" and not args.no_secondary and (args.Lx, args.Ly) == (10, 10):
             sys.path.insert(0, os.path.join(ROOT, "scripts"))
             try:
                 import secondary as _sec
@@ -799,11 +839,12 @@ def main():
                 except Exception as err:
                     projection[str(w_)] = {"error": f"{type(err).__name__}: {err}"}
         split16 = None
-        if mode == "single" and not args.no_secondary and not dry_run and qa.get_options().join_arith == "f32" \
+        if args.full and mode == "single" and not args.no_secondary and not dry_run and qa.get_options().join_arith == "f32" \
                 and tree is quad_tree:
             split16 = split_products_run(qa, dev, tree, xs, dtype, args, sync, ms, flops_step,
                                          shares=share_ms_of if (args.Lx, args.Ly) == (10, 10) else None)
-        cpu = None if (args.no_cpu or world > 1 or emulate) else cpu_baseline(args.D, args.Ly, args.seed, Lx=args.Lx, full=not args.no_cpu_full)   # N=1 only
+        cpu = None if (not args.full or args.no_cpu or world > 1 or emulate) else \
+            cpu_baseline(args.D, args.Ly, args.seed, Lx=args.Lx, full=not args.no_cpu_full)   # N=1 only
         nsl = plan.nslices if mode == "two_sided" else tree.nslices
         if mode == "single":
             workload, par = "unsliced, 1 GPU", "single"
@@ -852,7 +893,8 @@ def main():
             "value_useful_tflops": 2 * min(sweep_tree.contraction_cost(), quad_tree.contraction_cost()) / (dt / args.steps) / 1e12,
             "pct_mfma_peak_useful": 100.0 * 2 * min(sweep_tree.contraction_cost(), quad_tree.contraction_cost())
                                     / (dt / args.steps) / 1e12 / (MFMA_F32_PEAK_TF * world),
-            "result": _result_with_parity(res, args) if not emulate else
+            "result": (_result_with_parity(res, args) if args.full else {"mantissa": res[0], "exponent_log10": res[1]})
+                      if not emulate else
                       {"mantissa": res[0], "exponent_log10": res[1], "note": "ONE rank's block z_ij of the sum, not the network's value"},
             "roofline": roof,
             "cpu_baseline": cpu,

@@ -13,8 +13,8 @@ timeout 700 python -u -m pytest tests -m gpu -q -x --timeout 150 --timeout-metho
 echo "gpu tests rc=$? : $(tail -1 $OUT/gputest_$TAG.log)" >> $OUT/validate.log
 echo "== smoke" >> $OUT/validate.log
 timeout 90 python -c "import __graft_entry__ as g; g.smoke()" >> $OUT/validate.log 2>&1
-echo "== bench (default command)" >> $OUT/validate.log
-timeout 400 python bench.py --steps 10 > $OUT/bench_$TAG.json 2> $OUT/bench_$TAG.err
+echo "== bench (default command, with every extra: --full)" >> $OUT/validate.log
+timeout 400 python bench.py --full --steps 10 > $OUT/bench_$TAG.json 2> $OUT/bench_$TAG.err
 echo "bench rc=$? : $(cut -c1-220 $OUT/bench_$TAG.json)" >> $OUT/validate.log
 echo "== profiles" >> $OUT/validate.log
 timeout 500 bash scripts/collect_profiles.sh $TAG > $OUT/collect_$TAG.log 2>&1

@@ -8,7 +8,8 @@ module-level functions of ``quimb_amd``; ``quimb_amd.autoray_backend.register()`
 maintainer would register (fuse, norm_fro, the split drivers).  The device is the numpy plan interpreter of the
 CPU tests (this script runs in the build container only: /root/reference does not exist on the GPU box).
 
-Run by tests/test_dropin_reference.py in a subprocess; prints "DROPIN OK" when every check passed.
+Run by hand where quimb's sources are present (it is not part of the suite: they are not in this repository), and by
+scripts/verify_real_stack.py with ``--stack real``; prints "DROPIN OK" when every check passed.
 """
 import argparse
 import os

@@ -93,6 +93,65 @@ def test_bench_line_contract(emu, monkeypatch, argv, tree):
         assert got == pytest.approx(want, rel=1e-4)      # (fp32 inputs through the interpreter)
 
 
+def _count_contractions(monkeypatch):
+    import quimb_amd as qa
+
+    calls = [0]
+    plain_call = qa.TreeExecutor.__call__
+
+    def counted(self, *a, **k):
+        calls[0] += 1
+        return plain_call(self, *a, **k)
+
+    monkeypatch.setattr(qa.TreeExecutor, "__call__", counted)
+    return calls
+
+
+def test_bench_plain_run_is_lean(emu, monkeypatch):
+    """A run without ``--full`` contracts the network exactly warmup + steps times (a fixed tree: no untimed probe of the
+    other) and nothing beside: no CPU baseline, no oracle comparison, no extra profiling pass."""
+    calls = _count_contractions(monkeypatch)
+    d = _run(monkeypatch, ["--Lx", "4", "--Ly", "4", "--D", "3", "--steps", "3", "--warmup", "2", "--tree", "sweep"])
+    assert calls[0] == 2 + 3 and d["steps"] == 3 and d["warmup"] == 2
+    assert d["cpu_baseline"] is None and set(d["result"]) == {"mantissa", "exponent_log10"}
+    assert not {"secondary", "scaling_projection", "split_products_f16x3"} & set(d)
+
+
+def test_bench_full_keeps_the_extras(emu, monkeypatch):
+    """``--full``: the extras run after the timed region -- here the per-class roofline pass (one more contraction) and
+    the CPU baseline (bounded sample + the whole 4x4 network)."""
+    calls = _count_contractions(monkeypatch)
+    d = _run(monkeypatch, ["--Lx", "4", "--Ly", "4", "--D", "3", "--steps", "3", "--warmup", "2", "--tree", "sweep", "--full"])
+    assert calls[0] > 2 + 3
+    cpu = d["cpu_baseline"]
+    assert cpu["value"] > 0 and cpu["threads"] <= cpu["cores_usable"] <= cpu["cores"] and "full_network_seconds" in cpu
+
+
+@pytest.mark.parametrize("extra", [["--tree", "sweep"], ["--tree", "quadrant"], ["--emulate-world", "4"],
+                                   ["--sliced", "--slices", "9"]])
+def test_bench_dump_outputs(emu, monkeypatch, tmp_path, extra):
+    """``--dump-outputs DIR``: the last timed step's (mantissa, exponent) as .npy files in float32 / float64, the same
+    pair as the line's ``result``; a second run with the same arguments writes the same arrays (seeded inputs; the tree
+    is fixed -- ``--tree auto`` times both, and which one wins on the interpreter is noise)."""
+    D = "4" if "--emulate-world" in extra else "3"
+    argv = ["--Lx", "4", "--Ly", "4", "--D", D, "--steps", "2", "--warmup", "1"] + extra
+    d = _run(monkeypatch, argv + ["--dump-outputs", str(tmp_path / "a")])
+    _run(monkeypatch, argv + ["--dump-outputs", str(tmp_path / "b")])
+    import numpy as np
+
+    files = sorted(p.name for p in (tmp_path / "a").iterdir())
+    assert files == ["exponent_log10.npy", "mantissa.npy"]
+    arrs = {}
+    for name in files:
+        a, b = np.load(tmp_path / "a" / name), np.load(tmp_path / "b" / name)
+        assert a.dtype in (np.float32, np.float64) and a.dtype == b.dtype and a.shape == b.shape
+        assert np.array_equal(a, b)
+        arrs[name[:-4]] = a
+    assert arrs["exponent_log10"].dtype == np.float64
+    assert float(arrs["mantissa"].reshape(-1)[0]) == pytest.approx(d["result"]["mantissa"], rel=1e-6)
+    assert float(arrs["exponent_log10"]) == d["result"]["exponent_log10"]
+
+
 def _bench_worker(rank, world, port, outdir):
     import contextlib as cl
 
